@@ -29,8 +29,10 @@ pattern's own ceiling on this box), and an alternating A/B of rotating against s
         --master-port P bench.py --gpus N --steps K --warmup W
     python bench.py --host node --gpus N ...         # ONE process, rd_node_batch_* (what a Rust / C host calls)
 
-Prints ONE JSON line on rank 0.  `value` counts output pixels of all ranks over the max-over-ranks
-wall time of exactly K steps, inputs already resident in HBM.  `roofline` is the dominant kernel
+Prints ONE compact JSON line on rank 0 (a few KB: headline, `ms_per_step`, a small roofline, `cpu_baseline`'s value and
+`diagnosis` last); --record PATH writes the whole record, with everything named below, to PATH.  --dump-outputs DIR writes
+what the last timed step computed (histogram, a fixed sample of the ring's surfaces) as .npy files.  `value` counts output
+pixels of all ranks over the max-over-ranks wall time of exactly K steps, inputs already resident in HBM.  `roofline` is the dominant kernel
 (rd_develop_batch) against the 8 TB/s HBM3E peak with the algorithmic 18 B/px of BASELINE.md section 2;
 its launch duration is measured here with HIP events on the launch stream.  `cpu_baseline` is the
 oracle (oracle/develop_ref.c, a port -- the reference has no CPU path) on the host cores, rank 0,
@@ -97,6 +99,13 @@ def parse_args(argv=None):
                          "box probes after the region, pattern probe, descriptor A/B)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline budget")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (rank 0's share): "
+                         "histogram.npy (float64 [3, 256]) and surface_sample.npy (float32 [ring slots, pixels, 4], a fixed seeded "
+                         "sample of the same pixels of every ring surface, at most 48 MB)")
+    ap.add_argument("--record", metavar="PATH", default=None,
+                    help="write the full result record (every diagnosis and extra configuration) as JSON to PATH; stdout carries "
+                         "the compact result line only")
     return ap.parse_args(argv)
 
 
@@ -382,6 +391,64 @@ def verify_outputs(fmt_name, W, H, cfas, params_last, ring, n_frames, math_name)
         nb = info
         checked.append(i)
     return True, f"frames {checked}: {nb} row bands each bit-identical to the oracle"
+
+
+DUMP_SURFACE_BYTES = 48 << 20          # --dump-outputs: the surface sample's budget (float32), beside a 6 KiB histogram
+SURFACE_TORCH_DTYPE = {"f32": "float32", "f16": "float16", "u8": "uint8"}
+
+
+def dump_sample_pixels(np, W, H, n_slots):
+    """The pixels --dump-outputs samples from every ring surface: a fixed draw from SEED, sorted, without repeats."""
+    npx = W * H
+    n = min(npx, DUMP_SURFACE_BYTES // (16 * max(1, n_slots)))
+    return np.sort(np.random.default_rng(SEED).choice(npx, n, replace=False))
+
+
+def dump_outputs(torch, np, out_dir, fmt_name, W, H, ring, hist):
+    """--dump-outputs: what the last timed step handed its caller, as float32 / float64 .npy files.  Ring slot s holds the
+    last frame i of the step with i % len(ring) == s; every slot is sampled at the same pixels (dump_sample_pixels)."""
+    os.makedirs(out_dir, exist_ok=True)
+    idx = dump_sample_pixels(np, W, H, len(ring))
+    idx_t = torch.from_numpy(idx).to(ring[0].device)
+    dt = getattr(torch, SURFACE_TORCH_DTYPE[fmt_name])
+    sample = np.stack([r.view(dt).view(W * H, 4).index_select(0, idx_t).float().cpu().numpy() for r in ring])
+    files = {"surface_sample": sample.astype(np.float32)}
+    if hist is not None:
+        h = hist.cpu().numpy() if hasattr(hist, "cpu") else np.asarray(hist)
+        files["histogram"] = h.reshape(3, 256).astype(np.float64)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": {name: list(a.shape) for name, a in files.items()}}
+
+
+COMPACT_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "kernel_ms_per_step", "gap_ms_per_step",
+                "higher_is_better", "scaling", "vs_baseline", "dtype", "surface_dtype", "data", "verified", "verified_note",
+                "world_size_seen", "distinct_devices", "per_gpu_MPps_min", "per_gpu_MPps_max", "backend", "outputs_dumped")
+COMPACT_ROOFLINE_KEYS = ("bound", "bound_measured", "achieved", "peak", "unit", "frac", "frac_kernel", "frac_of_box_copy",
+                         "frac_of_box_pattern", "box_copy_GBps", "launch_us", "us_per_frame")
+COMPACT_LINE_MAX = 4096
+
+
+def compact_line(result):
+    """The stdout result line: the headline, a small roofline, the CPU baseline's value and the self-diagnosis (last key), a
+    few KB.  A driver that keeps only the tail of stdout must be able to parse it; the whole record goes to --record."""
+    line = {k: result[k] for k in COMPACT_KEYS if k in result}
+    cfg = result.get("config") or {}
+    line["config"] = {k: cfg[k] for k in ("frames_per_gpu", "width", "height", "surface", "math_mode", "launches_per_step") if k in cfg}
+    rf = result.get("roofline") or {}
+    line["roofline"] = {k: rf[k] for k in COMPACT_ROOFLINE_KEYS if k in rf}
+    if isinstance(result.get("cpu_baseline"), dict):
+        line["cpu_baseline"] = {k: result["cpu_baseline"].get(k) for k in ("value", "unit", "cores", "kind")}
+    if "diagnosis" in result:
+        line["diagnosis"] = result["diagnosis"]
+    return line
+
+
+def emit_result(result, args):
+    if args.record:
+        with open(args.record, "w") as f:
+            json.dump(result, f)
+    print(json.dumps(compact_line(result)), flush=True)
 
 
 def pmc_traffic(fmt_name, W, H, mode):
@@ -1402,6 +1469,9 @@ def run_ranks(args):
     dev_ms = ev0.elapsed_time(ev1)                         # HIP events on the launch stream
     elapsed_own = elapsed
     valu_ns = measure_valu_ns(ra, dev_index) if (rank == 0 and not args.no_box) else None     # right after the region: the clocks are up
+    dumped = None
+    if rank == 0 and args.dump_outputs:                    # before any diagnostic pass writes the ring or the histogram again
+        dumped = dump_outputs(torch, np, args.dump_outputs, args.format, W, H, ring, hist if with_hist else None)
 
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -1557,6 +1627,8 @@ def run_ranks(args):
                          "one frame array resubmitted every step (upload skipped)" if args.static_descriptors else
                          "steps rotate through three frame arrays (the slider stacks rotated by a third of the batch); librawdev caches "
                          "the last two arrays it saw, so every step uploads its descriptors", box=box, valu_ns=valu_ns, diag=diag)
+    if dumped:
+        result["outputs_dumped"] = dumped
     if rank == 0:
         # as-nccl: the duplicate-device rule applies to this run (nccl always; RAWDEV_DIAG_ASSUME_NCCL=1 lets the gloo
         # rehearsal on a one-GPU box prove that the rule fires)
@@ -1666,7 +1738,7 @@ def run_ranks(args):
             print(json.dumps(result), file=sys.stderr, flush=True)
             failed = True
         else:
-            print(json.dumps(result), flush=True)
+            emit_result(result, args)
     be.close()
     if world > 1:
         dist.barrier()                                     # rank 0 spent a second on the oracle check: leave together
@@ -1766,6 +1838,9 @@ def run_node(args):
         hist = nb.histogram_fetch()                        # every timed step's interval, summed (ABI 5; the read-backs landed before the synchronise)
         hist_steps = args.steps
 
+    dumped = None
+    if args.dump_outputs:                                  # device 0's ring; the histogram as rd_node_batch_histogram_fetch returned it
+        dumped = dump_outputs(torch, np, args.dump_outputs, args.format, W, H, per_dev[0][2], hist if with_hist else None)
     if with_hist:
         got = int(hist.sum())
         assert got == 3 * N * F * W * H * hist_steps, f"histogram sum {got} != {3 * N * F * W * H * hist_steps}"
@@ -1792,6 +1867,8 @@ def run_node(args):
                              "all": [round(x, 3) for x in step_ms] if len(step_ms) <= 32 else None,
                              "note": "host wall time of each step (develop + histogram, which synchronises)"}
     result["env"] = {k: os.environ.get(k) for k in DIAG_ENV + ("RD_NODE_REDUCE", "RAWDEV_RCCL_LIB")}
+    if dumped:
+        result["outputs_dumped"] = dumped
     if with_hist:
         # the histogram call on its own (per-device fold + all-reduce over RCCL when N > 1 + read-back + synchronise), idle devices
         lat = []
@@ -1804,7 +1881,7 @@ def run_node(args):
                                        "note": "rd_node_batch_histogram on idle devices: fold kernels + reduction + 6 KiB read-back + synchronise"}
     if N == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(W, H, args.cpu_seconds)
-    print(json.dumps(result), flush=True)
+    emit_result(result, args)
     nb.close()
 
 

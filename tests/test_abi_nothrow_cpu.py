@@ -74,7 +74,8 @@ CASES = [(_lib.FAULT_BAD_ALLOC, _lib.RD_ERR_OOM, "std::bad_alloc"), (_lib.FAULT_
          (_lib.FAULT_RUNTIME, _lib.RD_ERR_INTERNAL, "injected fault at"), (_lib.FAULT_FOREIGN, _lib.RD_ERR_INTERNAL, "unknown C++ exception")]
 
 
-@pytest.mark.parametrize("kind,code,text", CASES)
+# ids: "::" is pytest's node-id separator, so it may not appear inside a case's id ("std::bad_alloc" -> "std_bad_alloc")
+@pytest.mark.parametrize("kind,code,text", CASES, ids=lambda v: v.replace("::", "_") if isinstance(v, str) else None)
 def test_injected_exceptions_become_statuses(disarm, kind, code, text):
     L = _lib.lib()
     p = _lib.RdEditParams()

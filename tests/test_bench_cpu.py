@@ -299,3 +299,44 @@ def test_buffers_can_be_views_into_one_arena():
     assert p0 == p1 and all(torch.equal(x, y) for x, y in zip(c0, c1))
     d = [c.data_ptr() for c in c1]
     assert d[0] % (2 << 20) == 0 and d[1] - d[0] == (2 << 20) + 4096 == d[2] - d[1]
+
+
+def test_stdout_line_is_compact_and_the_record_is_whole(tmp_path, capsys):
+    """The stdout line of a fully populated run (every diagnosis and extra configuration) stays a few KB and carries the
+    headline, ms_per_step and the diagnosis; --record keeps the whole record."""
+    with open(os.path.join(ROOT, "profiles", "r06_final_bench.json")) as f:
+        full = json.load(f)
+    assert len(json.dumps(full)) > 20000
+    args = bench.parse_args(["--record", str(tmp_path / "r.json")])
+    bench.emit_result(full, args)
+    lines = capsys.readouterr().out.splitlines()
+    assert len(lines) == 1 and len(lines[0]) < bench.COMPACT_LINE_MAX
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "verified"):
+        assert line[k] == full[k], k
+    assert line["roofline"]["frac"] == full["roofline"]["frac"] and line["cpu_baseline"]["value"] == full["cpu_baseline"]["value"]
+    assert list(line)[-1] == "diagnosis" and line["diagnosis"] == full["diagnosis"]
+    assert json.load(open(tmp_path / "r.json")) == full
+
+
+def test_dump_outputs_writes_float_arrays_of_a_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+    W, H = 40, 30
+    a = bench.parse_args(["--dump-outputs", str(tmp_path / "d"), "--steps", "7"])
+    assert a.dump_outputs == str(tmp_path / "d") and a.steps == 7 and bench.parse_args([]).dump_outputs is None
+    idx = bench.dump_sample_pixels(np, W, H, 3)
+    assert np.array_equal(idx, bench.dump_sample_pixels(np, W, H, 3)) and len(np.unique(idx)) == len(idx) == W * H
+    big = bench.dump_sample_pixels(np, 6016, 4016, 8)
+    assert len(big) * 8 * 16 <= bench.DUMP_SURFACE_BYTES and big[-1] < 6016 * 4016
+    for fmt, dt in (("f32", torch.float32), ("f16", torch.float16), ("u8", torch.uint8)):
+        surf = [torch.arange(W * H * 4).remainder(251).to(dt).add(s).view(torch.uint8) for s in range(3)]
+        hist = torch.arange(768, dtype=torch.int64)
+        info = bench.dump_outputs(torch, np, str(tmp_path / fmt), fmt, W, H, surf, hist)
+        s = np.load(tmp_path / fmt / "surface_sample.npy")
+        h = np.load(tmp_path / fmt / "histogram.npy")
+        assert s.dtype == np.float32 and s.shape == (3, W * H, 4) and h.dtype == np.float64 and h.shape == (3, 256)
+        assert info["files"] == {"surface_sample": [3, W * H, 4], "histogram": [3, 256]}
+        for k in range(3):
+            assert np.array_equal(s[k], surf[k].view(dt).view(W * H, 4)[torch.from_numpy(idx)].float().numpy())
+        assert np.array_equal(h.reshape(-1), np.arange(768))

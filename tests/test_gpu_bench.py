@@ -27,11 +27,23 @@ def _bench_raw(argv, extra_env, timeout=900):
 
 
 def _bench(argv, extra_env, timeout=900):
-    out = _bench_raw(argv, extra_env, timeout)
-    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
-    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
-    assert len(lines) == 1, out.stdout
-    return json.loads(lines[0])
+    """The whole record (--record), after checking the compact stdout line against it."""
+    import tempfile
+    with tempfile.TemporaryDirectory() as td:
+        record = os.path.join(td, "record.json")
+        out = _bench_raw(argv + ["--record", record], extra_env, timeout)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+        lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, out.stdout
+        assert len(lines[0]) < 4096, len(lines[0])             # fits the tail of stdout a driver keeps
+        with open(record) as f:
+            r = json.load(f)
+    line = json.loads(lines[0])
+    for k in ("value", "n_gpus", "steps", "warmup", "ms_per_step", "verified"):
+        assert line[k] == r[k], k
+    assert line["ms_per_step"] > 0 and line["steps"] == int(argv[argv.index("--steps") + 1])
+    assert line.get("diagnosis") == r.get("diagnosis")
+    return r
 
 
 def test_bare_multi_gpu_call_launches_its_own_ranks(gpu_lib):
@@ -160,6 +172,43 @@ def test_single_gpu_line_carries_the_other_configs(gpu_lib):
     assert len(json.dumps(dg)) < 6000                              # fits the tail a driver keeps
     q = _bench(["--frames", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--no-diagnose"], {})
     assert q["verified"] is True and q["kernel_ms_per_step"] is None and q["roofline"]["launches"] is None and q["clocks"] is None
+
+
+def test_dump_outputs_are_the_last_steps_surfaces_and_histogram(gpu_lib, refc, tmp_path):
+    """--dump-outputs: the same arguments give the same files, bit for bit; the sampled pixels of a ring slot are the oracle's
+    for the frame the last step wrote there, and the histogram counts every pixel of one step."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    import raweditor_amd as ra
+    W, H, F, steps, warmup = 1024, 768, 16, 3, 1
+    argv = ["--frames", str(F), "--width", str(W), "--height", str(H), "--steps", str(steps), "--warmup", str(warmup),
+            "--no-cpu-baseline", "--no-extra", "--no-diagnose", "--no-alt-math", "--no-box"]
+    got = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = _bench(argv + ["--dump-outputs", str(d)], {})
+        assert r["verified"] is True and r["outputs_dumped"]["dir"] == str(d)
+        got.append({n: np.load(d / f"{n}.npy") for n in ("surface_sample", "histogram")})
+    ring = 8
+    idx = bench.dump_sample_pixels(np, W, H, ring)
+    for g in got:
+        assert g["surface_sample"].dtype == np.float32 and g["surface_sample"].shape == (ring, len(idx), 4)
+        assert g["histogram"].dtype == np.float64 and g["histogram"].shape == (3, 256)
+        assert g["histogram"].sum() == 3 * F * W * H
+    for n in ("surface_sample", "histogram"):
+        assert np.array_equal(got[0][n], got[1][n]), n
+    # slot 3 holds frame F - ring + 3 with the stacks of the last step's frame array (rotated by (warmup + steps - 1) % 3)
+    import torch
+    params = [ra.EditParams.random(np.random.default_rng([bench.SEED, f])) for f in range(F)]      # bench.make_batch's stacks
+    last = bench.rotated_stacks(params, (warmup + steps - 1) % 3)
+    i = F - ring + 3
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(bench.SEED + i)
+    cfa = torch.randint(0, 4096, (H, W), generator=g, device="cuda:0", dtype=torch.int16).cpu().numpy().view(np.uint16)
+    u = refc.make_uniforms({f: getattr(last[i], f) for f in ra.FIELDS}, bench.WB, bench.CM)
+    exp = refc.render_f32(cfa, u).reshape(-1, 4)[idx]
+    assert np.array_equal(got[0]["surface_sample"][3].view(np.uint32), exp.view(np.uint32))
 
 
 def test_measure_hbm_sizes(gpu_lib):
