@@ -346,6 +346,33 @@ int rd_exporter_submit_host(rd_exporter *e, const rd_frame *frame, const uint16_
 int rd_exporter_wait(rd_exporter *e, uint32_t slot, const void **data, size_t *len);
 int rd_exporter_release(rd_exporter *e, uint32_t slot);
 
+/* ---- cache tiers (reference src/raw/processor.rs:13-15, :67-88) ------------------------- */
+/* The Library grid's and the Develop view's images: the frame's RGBA8 export codes -- exactly the bytes rd_batch_develop
+ * (RD_FMT_RGBA_U8, strict arithmetic) produces for it -- resampled by a separable Lanczos3 filter, horizontal pass first, in
+ * f32 without contraction, each byte round_half_away(clamp(v, 0, 255)).  The reference resizes its embedded JPEG with
+ * image::imageops::resize(.., FilterType::Lanczos3) into the boxes (256, 2560), (384, 3840) and (1280, 12800).
+ * rd_tier_dims: no device needed; the size of a W x H frame's tier in a box_w x box_h box by resize's fit rule (ratio =
+ * min(box_w / W, box_h / H) in f64, each side round_half_away(side * ratio), at least 1).
+ * rd_tier_weights: no device needed; the exact tables the kernels use for one pass of n_in samples to n_out: output j
+ * takes samples left[j] .. left[j] + count[j] - 1 with the next count[j] weights of w (packed back to back).  *w_needed
+ * receives the number of weights; left / count (n_out entries each) and w (w_cap floats) may be NULL (a sizing call). */
+typedef struct rd_tiers rd_tiers;
+int rd_tier_dims(uint32_t width, uint32_t height, uint32_t box_w, uint32_t box_h, uint32_t *w, uint32_t *h);
+int rd_tier_weights(uint32_t n_in, uint32_t n_out, uint32_t *left, uint32_t *count, float *w, size_t w_cap, size_t *w_needed);
+/* A tiers context: frames of one size on one device, 1 to 4 tiers (box_w[i] x box_h[i]), RD_FMT_RGBA_U8 or RD_FMT_RGB_U8
+ * (any other format: RD_ERR_UNSUPPORTED).  Any width and height from 1 up, odd included, up to a width of 18494 (the
+ * developed row pair lives in one CU's LDS; wider: RD_ERR_UNSUPPORTED); a tier side is at most 65536.  The context owns the
+ * weight tables and the f32 scratch between the two passes (sized so that a launch's scratch stays in the Infinity Cache). */
+int rd_tiers_create(int device, uint32_t width, uint32_t height, uint32_t format, uint32_t n_tiers, const uint32_t *box_w,
+                    const uint32_t *box_h, rd_tiers **out);
+void rd_tiers_destroy(rd_tiers *t);                        /* NULL is a no-op */
+int rd_tiers_info(const rd_tiers *t, uint32_t tier, uint32_t *w, uint32_t *h);
+/* Enqueue the develop + tiers of n_frames frames on `stream`; not synchronised.  tier_dev holds n_frames x n_tiers device
+ * pointers, frame-major (frame i's tier k at [i * n_tiers + k]; w x h x bytes-per-pixel each, RGBA8 4-byte aligned);
+ * frames[i].out_dev is ignored.  Both arrays are copied before the call returns.  Strict arithmetic only.  One context
+ * serves one stream (its scratch is reused launch after launch), as a batch context does. */
+int rd_tiers_develop(rd_tiers *t, const rd_frame *frames, size_t n_frames, void *const *tier_dev, void *stream);
+
 /* ---- self-test ----------------------------------------------------------------------------- */
 /* The RGBA8 / RGB8 surfaces (the reference's target format, pipeline.rs:322) compute their 8-bit codes with a shortcut
  * (hardware log2/exp2, the pinned evaluation only near a code boundary).  rd_selftest_q8 runs that
@@ -435,7 +462,7 @@ int rd_debug_node_histogram_of(rd_node_batch *nb, uint32_t index, uint64_t hist[
 /* Fault injection: proves that nothing thrown inside the library crosses this boundary.  Arms ONE fault: the (after + 1)-th
  * passage through a fault point named `site` throws once, then the fault disarms itself.  Fault points: every entry point
  * under its own name ("rd_batch_develop"), the real allocation / thread-start sites ("pipeline.lanes", "batch.descs",
- * "node.share", "node.thread", "scratch.entry", "exporter.slots"), "*" = whichever comes first.  site NULL or kind 0 disarms.
+ * "node.share", "node.thread", "scratch.entry", "exporter.slots", "tiers.tables", "tiers.launch"), "*" = whichever comes first.  site NULL or kind 0 disarms.
  * The same through the environment, read when the library is loaded: RD_FAULT_INJECT=site:kind[:after]. */
 typedef enum rd_fault_kind {
     RD_FAULT_NONE = 0,

@@ -341,4 +341,35 @@ private:
     rd_node_batch *h_ = nullptr;
 };
 
+// Cache tiers (rd_tiers_*; reference raw/processor.rs makes them from the embedded JPEG with a Lanczos3 resize): the developed
+// frame resampled into up to four boxes, RGBA8 or RGB8, on the device.  DESIGN.md section 11 has the numerical contract.
+class Tiers {
+public:
+    Tiers(int device, uint32_t width, uint32_t height, rd_format format, const std::vector<std::pair<uint32_t, uint32_t>> &boxes)
+    {
+        std::vector<uint32_t> bw, bh;
+        for (const auto &b : boxes) { bw.push_back(b.first); bh.push_back(b.second); }
+        check(rd_tiers_create(device, width, height, format, (uint32_t)boxes.size(), bw.data(), bh.data(), &h_));
+        for (uint32_t k = 0; k < (uint32_t)boxes.size(); ++k) {
+            uint32_t w = 0, h = 0;
+            check(rd_tiers_info(h_, k, &w, &h));
+            dims_.emplace_back(w, h);
+        }
+    }
+    Tiers(const Tiers &) = delete;
+    Tiers &operator=(const Tiers &) = delete;
+    ~Tiers() { rd_tiers_destroy(h_); }
+    const std::vector<std::pair<uint32_t, uint32_t>> &dims() const { return dims_; }
+    // tier_dev: frames.size() x dims().size() device pointers, frame-major; enqueued on `stream`, not synchronised
+    void develop(const std::vector<rd_frame> &frames, const std::vector<void *> &tier_dev, void *stream = nullptr)
+    {
+        if (tier_dev.size() != frames.size() * dims_.size()) throw Error(RD_ERR_INVALID_ARG, "Tiers::develop: one pointer per frame and tier");
+        check(rd_tiers_develop(h_, frames.data(), frames.size(), tier_dev.data(), stream));
+    }
+
+private:
+    rd_tiers *h_ = nullptr;
+    std::vector<std::pair<uint32_t, uint32_t>> dims_;
+};
+
 }  // namespace rawdev

@@ -80,6 +80,13 @@ def init_schema(conn: sqlite3.Connection) -> None:
     conn.commit()
 
 
+def set_image_cache_paths(conn: sqlite3.Connection, image_id: int, thumb: str, instant: str, working: str) -> None:
+    """Library::set_image_cache_paths (library.rs:372-391): the three cache tier paths of an image, cache_status 'cached'."""
+    conn.execute("UPDATE images SET cache_status = 'cached', cache_path_thumb = ?1, cache_path_instant = ?2, "
+                 "cache_path_working = ?3 WHERE id = ?4", (str(thumb), str(instant), str(working), int(image_id)))
+    conn.commit()
+
+
 @dataclasses.dataclass
 class ManifestEntry:
     image_id: int
