@@ -373,6 +373,35 @@ int rd_tiers_info(const rd_tiers *t, uint32_t tier, uint32_t *w, uint32_t *h);
  * serves one stream (its scratch is reused launch after launch), as a batch context does. */
 int rd_tiers_develop(rd_tiers *t, const rd_frame *frames, size_t n_frames, void *const *tier_dev, void *stream);
 
+/* ---- baseline JPEG encoder (reference main.rs:1744-1799 export, raw/processor.rs:67-88 cache tiers) ---- */
+/* RGB8 / RGBA8 device surfaces -> baseline sequential JFIF files on the device, libjpeg's default compression path byte for
+ * byte: IJG integer RGB -> YCbCr (alpha ignored), 4:2:0 or 4:4:4, the islow DCT, Annex K quantisation tables scaled by the IJG
+ * quality rule (1..100, clamped to 1..255), the standard Huffman tables, a restart interval of R MCUs (1..65535; DRI + RSTn).
+ * Any width and height from 1 to 65535.
+ * rd_jpeg_header: no device needed; the exact bytes before the entropy-coded data (SOI .. SOS).  *len receives the length;
+ * buf NULL is a sizing call, a cap below the length is RD_ERR_INVALID_ARG. */
+typedef enum rd_jpeg_subsampling {
+    RD_JPEG_420 = 0,            /* Y 2x2, Cb 1x1, Cr 1x1 (libjpeg's default) */
+    RD_JPEG_444 = 1             /* every component 1x1 */
+} rd_jpeg_subsampling;
+typedef struct rd_jpeg rd_jpeg;
+int rd_jpeg_header(uint32_t width, uint32_t height, uint32_t quality, uint32_t subsampling, uint32_t restart_mcus,
+                   uint8_t *buf, size_t cap, size_t *len);
+/* An encoder context: frames of one size and format (RD_FMT_RGB_U8 or RD_FMT_RGBA_U8; any other: RD_ERR_UNSUPPORTED) on one
+ * device.  It owns the tables, the header and the scratch between its kernels, sized so that a launch's scratch stays bounded. */
+int rd_jpeg_create(int device, uint32_t width, uint32_t height, uint32_t format, uint32_t quality, uint32_t subsampling,
+                   uint32_t restart_mcus, rd_jpeg **out);
+void rd_jpeg_destroy(rd_jpeg *j);                          /* NULL is a no-op */
+/* max_bytes: a true worst case of one frame's file (the tables' longest codes, every byte stuffed, markers, header); either
+ * pointer may be NULL. */
+int rd_jpeg_info(const rd_jpeg *j, size_t *max_bytes, size_t *header_bytes);
+/* Enqueue the encode of n_frames frames on `stream`; not synchronised.  src_dev[i]: frame i's surface, rows src_pitch bytes
+ * apart (at least width x bytes-per-pixel); dst_dev[i]: dst_cap bytes (at least max_bytes, else RD_ERR_INVALID_ARG);
+ * len_dev: n_frames device u64, 8-byte aligned, frame i's file length.  Both pointer arrays are copied before the call
+ * returns.  One context serves one stream (its scratch is reused launch after launch). */
+int rd_jpeg_encode(rd_jpeg *j, const void *const *src_dev, size_t n_frames, size_t src_pitch, void *const *dst_dev,
+                   size_t dst_cap, uint64_t *len_dev, void *stream);
+
 /* ---- self-test ----------------------------------------------------------------------------- */
 /* The RGBA8 / RGB8 surfaces (the reference's target format, pipeline.rs:322) compute their 8-bit codes with a shortcut
  * (hardware log2/exp2, the pinned evaluation only near a code boundary).  rd_selftest_q8 runs that
@@ -462,7 +491,8 @@ int rd_debug_node_histogram_of(rd_node_batch *nb, uint32_t index, uint64_t hist[
 /* Fault injection: proves that nothing thrown inside the library crosses this boundary.  Arms ONE fault: the (after + 1)-th
  * passage through a fault point named `site` throws once, then the fault disarms itself.  Fault points: every entry point
  * under its own name ("rd_batch_develop"), the real allocation / thread-start sites ("pipeline.lanes", "batch.descs",
- * "node.share", "node.thread", "scratch.entry", "exporter.slots", "tiers.tables", "tiers.launch"), "*" = whichever comes first.  site NULL or kind 0 disarms.
+ * "node.share", "node.thread", "scratch.entry", "exporter.slots", "tiers.tables", "tiers.launch", "jpeg.scratch",
+ * "jpeg.launch"), "*" = whichever comes first.  site NULL or kind 0 disarms.
  * The same through the environment, read when the library is loaded: RD_FAULT_INJECT=site:kind[:after]. */
 typedef enum rd_fault_kind {
     RD_FAULT_NONE = 0,

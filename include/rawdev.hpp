@@ -372,4 +372,42 @@ private:
     std::vector<std::pair<uint32_t, uint32_t>> dims_;
 };
 
+// Baseline JPEG (rd_jpeg_*): RGB8 / RGBA8 device surfaces -> JFIF files on the device, libjpeg's default compression path byte
+// for byte.  DESIGN.md section 12 has the contract.
+class Jpeg {
+public:
+    Jpeg(int device, uint32_t width, uint32_t height, rd_format format = RD_FMT_RGB_U8, uint32_t quality = 90,
+         rd_jpeg_subsampling subsampling = RD_JPEG_420, uint32_t restart_mcus = 32)
+    {
+        check(rd_jpeg_create(device, width, height, format, quality, subsampling, restart_mcus, &h_));
+        check(rd_jpeg_info(h_, &max_bytes_, &header_bytes_));
+    }
+    Jpeg(const Jpeg &) = delete;
+    Jpeg &operator=(const Jpeg &) = delete;
+    ~Jpeg() { rd_jpeg_destroy(h_); }
+    size_t max_bytes() const { return max_bytes_; }         // each destination buffer holds at least this many bytes
+    size_t header_bytes() const { return header_bytes_; }
+    // src_dev / dst_dev: one device pointer per frame; len_dev: one device u64 per frame.  Enqueued on `stream`, not synchronised.
+    void encode(const std::vector<const void *> &src_dev, size_t src_pitch, const std::vector<void *> &dst_dev, size_t dst_cap,
+                uint64_t *len_dev, void *stream = nullptr)
+    {
+        if (src_dev.size() != dst_dev.size()) throw Error(RD_ERR_INVALID_ARG, "Jpeg::encode: one destination per frame");
+        check(rd_jpeg_encode(h_, src_dev.data(), src_dev.size(), src_pitch, dst_dev.data(), dst_cap, len_dev, stream));
+    }
+    // no device: the exact bytes before the entropy-coded data
+    static std::vector<uint8_t> header(uint32_t width, uint32_t height, uint32_t quality = 90,
+                                       rd_jpeg_subsampling subsampling = RD_JPEG_420, uint32_t restart_mcus = 32)
+    {
+        size_t n = 0;
+        check(rd_jpeg_header(width, height, quality, subsampling, restart_mcus, nullptr, 0, &n));
+        std::vector<uint8_t> out(n);
+        check(rd_jpeg_header(width, height, quality, subsampling, restart_mcus, out.data(), out.size(), &n));
+        return out;
+    }
+
+private:
+    rd_jpeg *h_ = nullptr;
+    size_t max_bytes_ = 0, header_bytes_ = 0;
+};
+
 }  // namespace rawdev

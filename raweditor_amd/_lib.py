@@ -111,6 +111,11 @@ PROTOTYPES = {
     "rd_tiers_destroy": (None, [_VP]),
     "rd_tiers_info": (_I, [_VP, _U32, C.POINTER(_U32), C.POINTER(_U32)]),
     "rd_tiers_develop": (_I, [_VP, C.POINTER(RdFrame), _SZ, C.POINTER(_VP), _VP]),
+    "rd_jpeg_header": (_I, [_U32, _U32, _U32, _U32, _U32, _VP, _SZ, C.POINTER(_SZ)]),
+    "rd_jpeg_create": (_I, [_I, _U32, _U32, _U32, _U32, _U32, _U32, C.POINTER(_VP)]),
+    "rd_jpeg_destroy": (None, [_VP]),
+    "rd_jpeg_info": (_I, [_VP, C.POINTER(_SZ), C.POINTER(_SZ)]),
+    "rd_jpeg_encode": (_I, [_VP, C.POINTER(_VP), _SZ, _SZ, C.POINTER(_VP), _SZ, _VP, _VP]),
     "rd_selftest_q8": (_I, [_I, C.POINTER(C.c_uint64), C.POINTER(_U32), C.POINTER(C.c_uint64), C.POINTER(C.c_float)]),
     "rd_selftest_q8_codes": (_I, [_I, _U32, _U32, _VP]),
     "rd_selftest_q8_lut": (_I, [_I, C.POINTER(C.c_uint64), C.POINTER(_U32)]),

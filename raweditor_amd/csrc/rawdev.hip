@@ -11,7 +11,8 @@
 // There is no CPU compute path in this library: every render is a gfx950 kernel launch.
 // Layout (one translation unit): this file = errors, device bookkeeping, launch plumbing, ingest helper, plumbing, test hooks;
 // rd_host_pipeline.inl = rd_pipeline; rd_host_batch.inl = rd_batch / rd_node_batch / rd_exporter; rd_host_diag.inl = self-tests
-// and measurement aids; rd_host_tiers.inl = the cache tiers (rd_tier_*, rd_tiers_*).
+// and measurement aids; rd_host_tiers.inl = the cache tiers (rd_tier_*, rd_tiers_*); rd_host_jpeg.inl = the baseline
+// JPEG encoder (rd_jpeg_*).
 #include <hip/hip_runtime.h>
 
 #include <dlfcn.h>
@@ -38,6 +39,7 @@
 #include "rd_kernels.h"
 #include "rd_ljpeg.h"
 #include "rd_tiers.h"
+#include "rd_jpeg.h"
 
 // ------------------------------------------------------------------------------------------------
 // errors
@@ -706,6 +708,7 @@ static int rd_enqueue_render(const rd_launch_cfg &cfg, const uint16_t *cfa, uint
 #include "rd_host_batch.inl"
 #include "rd_host_diag.inl"
 #include "rd_host_tiers.inl"
+#include "rd_host_jpeg.inl"
 
 // ------------------------------------------------------------------------------------------------
 // ingest helper: lossless-JPEG tiles of compressed DNGs (host code; rd_ljpeg.h)

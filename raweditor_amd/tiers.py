@@ -156,3 +156,70 @@ def write_catalog_tiers(conn, image_id: int, tiers: Sequence, cache_root: str, q
         paths.append(path)
     catalog.set_image_cache_paths(conn, image_id, *paths)
     return tuple(paths)
+
+
+def render_tier_jpegs(cfa, width: int, height: int, params: EditParams, wb, cm, black_level: int = 0, quality: int = 90,
+                      subsampling="4:2:0", restart_mcus: int = 32, device: int = 0,
+                      matrix_layout: int = _lib.MATRIX_REFERENCE) -> Tuple[bytes, bytes, bytes]:
+    """One frame's three reference tiers (thumb, instant, working) as JPEG files, made on the device: rd_tiers_develop into
+    RGB8 surfaces, then rd_jpeg_encode (DESIGN.md sections 11 and 12).  The bytes are the ones libjpeg's default path
+    writes for render_tiers(..., fmt=FMT_RGB_U8)'s arrays."""
+    import numpy as np
+    from .jpeg import JpegEncoder, encode_device
+    cfa = np.ascontiguousarray(np.asarray(cfa, np.uint16).reshape(int(height), int(width)))
+    L = _lib.lib()
+    r = TierRenderer(device, width, height, REFERENCE_TIERS, _lib.FMT_RGB_U8)
+    bufs = []
+    try:
+        cfa_dev = C.c_void_p()
+        check(L.rd_device_malloc(device, cfa.nbytes, C.byref(cfa_dev)))
+        bufs.append(cfa_dev)
+        check(L.rd_memcpy_h2d(device, cfa_dev, cfa.ctypes.data_as(C.c_void_p), cfa.nbytes))
+        outs = []
+        for k in range(len(r.dims)):
+            p = C.c_void_p()
+            check(L.rd_device_malloc(device, r.tier_bytes(k), C.byref(p)))
+            bufs.append(p)
+            outs.append(p)
+        frames = (RdFrame * 1)()
+        frames[0].cfa_dev = cfa_dev.value
+        frames[0].out_dev = None
+        frames[0].params = params.to_c()
+        frames[0].wb_multipliers[:] = [float(x) for x in wb]
+        frames[0].color_matrix[:] = [float(x) for x in cm]
+        frames[0].black_level = int(black_level)
+        frames[0].matrix_layout = int(matrix_layout)
+        r.develop(frames, [p.value for p in outs])              # the same (null) stream as the encodes below
+        files = []
+        for k, p in enumerate(outs):
+            w, h = r.dims[k]
+            enc = JpegEncoder(device, w, h, _lib.FMT_RGB_U8, quality, subsampling, restart_mcus)
+            try:
+                files.append(encode_device(enc, [p])[0])
+            finally:
+                enc.close()
+        return tuple(files)
+    finally:
+        for p in bufs:
+            L.rd_device_free(device, p)
+        r.close()
+
+
+def write_catalog_tier_jpegs(conn, image_id: int, jpegs: Sequence[bytes], cache_root: str) -> Tuple[str, str, str]:
+    """Store three JPEG files (thumb, instant, working, as render_tier_jpegs returns them) at the paths write_catalog_tiers
+    uses, {cache_root}/{thumb,instant,working}/{image_id}.jpg, and record them (catalog.set_image_cache_paths)."""
+    from . import catalog
+    if len(jpegs) != 3:
+        raise ValueError(f"three JPEG files (thumb, instant, working) expected, got {len(jpegs)}")
+    paths = []
+    for name, data in zip(TIER_NAMES, jpegs):
+        if not bytes(data[:2]) == b"\xff\xd8":
+            raise ValueError(f"the {name} tier is not a JPEG file")
+        d = os.path.join(cache_root, name)
+        os.makedirs(d, exist_ok=True)
+        path = os.path.join(d, f"{int(image_id)}.jpg")
+        with open(path, "wb") as f:
+            f.write(bytes(data))
+        paths.append(path)
+    catalog.set_image_cache_paths(conn, image_id, *paths)
+    return tuple(paths)
